@@ -28,8 +28,12 @@ with all environments in phase (`synchronised_window`; `phases` splits it into f
 rasterisation of step t next to the substeps of step t+1, and SUSTAINED full episodes (`episodes`: reset -> 30 settling steps ->
 450 policy steps on every slot, observation sink on; eval_policy.py:65-267).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the fused physics substep) and `cpu_baseline`
-(the oracle — a CPU restatement of the reference algorithm, kind "port" — on a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports `value` / `ms_per_step` with the
+window's own per-step log.  `--full` adds everything that takes work of its own: the parity gate before the window, the synchronised
+window and its `phases`, the throughput-mode and closed-loop comparisons, `roofline` (dominant kernel = the fused physics substep) with
+its per-kernel checks, the raster stage timing, `cpu_baseline` (the oracle — a CPU restatement of the reference algorithm, kind "port"
+— on a bounded sample) and the sustained `episodes`.  `--dump-outputs DIR` writes what the timed path computed in its last step
+(dump_outputs).
 """
 import argparse
 import json
@@ -229,6 +233,42 @@ def sustained_episodes(config, dev, seed, n_env, substeps, res, per_slot, steps,
     return out
 
 
+DUMP_ELEMS = 15 << 20   # float32 elements written by --dump-outputs in all (60 MiB)
+
+
+def dump_outputs(ro, out_dir):
+    """--dump-outputs: what a caller of the timed path receives after its last step — get_obs() (the fixed and wrist cameras'
+    images [E,3,H,W] and depths [E,1,H,W], the robot state) and the particle state the step advanced (x, v [E,N,3]) — as
+    out_dir/<name>.npy, float32.  Every array gets an equal share of DUMP_ELEMS; a larger one is written as a fixed sample of
+    its flattened elements: sorted indices drawn without replacement from numpy's default_rng(0), the same for the same shape in
+    every run.  Returns {name: [shape written, shape of the array]}."""
+    import numpy as np
+    import torch
+
+    obs = ro.get_obs()
+    arrays = {}
+    for key in ("image", "depth", "image_wrist", "depth_wrist"):
+        for v, t in enumerate(obs[f"{key}_list"]):
+            arrays[f"{key}_{v}"] = t
+    for k, t in (obs["robot"] or {}).items():
+        arrays[f"robot_{k}"] = t
+    arrays["particles_x"], arrays["particles_v"] = ro.phys.x, ro.phys.v
+    if torch.device(ro.device).type == "cuda":
+        torch.cuda.synchronize(ro.device)
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_ELEMS // len(arrays)
+    shapes = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1).float()
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu().numpy() if flat.numel() < t.numel() else flat.cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        shapes[name] = [list(a.shape), list(t.shape)]
+    return shapes
+
+
 class StubRollout:
     """CPU stand-in for BatchedRollout: the launcher / barrier / MAX / all-gather / JSON path of this file without a GPU
     (tests/test_distributed_gloo.py drives `bench.py --stub --gpus 2` through the same self-launch as the real bench)."""
@@ -287,8 +327,8 @@ def main():
     ap.add_argument("--no-pipelined", action="store_true", help="skip the throughput-mode comparison that follows the timed window")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--stub", action="store_true", help="CPU stand-in workload over gloo (launcher test)")
-    ap.add_argument("--no-parity-gate", action="store_true", help="skip the parity gate that precedes the timed window (default: on; a failing gate "
-                                                                  "withholds `value`)")
+    ap.add_argument("--no-parity-gate", action="store_true", help="skip the parity gate that precedes the timed window (default: on with --full; a failing "
+                                                                  "gate withholds `value`)")
     ap.add_argument("--dephase", type=int, default=-1, help="the timed window's environments run the action trace (e K) // E steps late — they close their "
                                                             "grippers one after the other across the window instead of all at its middle (episodes of "
                                                             "eval_policy_parallel.py do not share a phase).  -1: K = --steps (default), 0: all environments "
@@ -303,6 +343,11 @@ def main():
     ap.add_argument("--episode-steps", type=int, default=0, help="policy steps per episode of the sustained measurement (0: the reference's: sloth 450, rope 900, T 1800)")
     ap.add_argument("--sink", default=None, help="directory: also run the observation sink (row f4) every step — packed 8-bit frames + state "
                                                  "to pinned ring buffers, JPEG / pickle written by a host thread; not part of the headline")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: the parity gate, the synchronised window, the "
+                                                        "throughput-mode and closed-loop comparisons, roofline and per-kernel checks, raster stage "
+                                                        "timing, the CPU baseline and the sustained episodes (the --no-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                                                                        "(float32, at most 60 MiB; rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     from r2s_hip import dist as rdist
@@ -332,9 +377,9 @@ def main():
     # gated on a 9-environment batch — the large-batch layout with two concurrent kernel chains, the flavour family the window
     # times (the first and the last environment, one per chain, each against its own oracle) —, a one-environment window on one
     # environment (the resident layout).  `parity_gate.flavour / chains / layout` say what ran.  Rank 0 only; the other ranks wait
-    # at the first barrier.
+    # at the first barrier.  --full only.
     gate = None
-    if not args.no_parity_gate and rank == 0:
+    if args.full and not args.no_parity_gate and rank == 0:
         from oracle import parity_gate
         try:
             n_bench = args.envs if args.envs is not None else CONFIGS[args.config][3]
@@ -409,6 +454,7 @@ def main():
         sink_report = {"frames_written": sink.frames_written, "steps_written": sink.steps_written, "producer_stalls": sink.stalls,
                        "drain_after_window_s": time.perf_counter() - t1, "format": sink.ext,
                        "note": "submit() only enqueues a pack kernel + one async D2H per step; encoding and file writes run in worker processes"}
+    dumped = dump_outputs(ro, args.dump_outputs) if args.dump_outputs and rank == 0 else None   # the last timed step, before anything below moves `ro` on
     # N > 1: slowest rank's time (MAX) and the metric all-gather of north_star — one fixed-size record per rank
     elapsed = rdist.max_over_ranks(elapsed, dev)
     n_success = int(ro.success_flags().sum().item())  # device-side task predicate (row f4); outside the timed region
@@ -417,9 +463,10 @@ def main():
 
     # ---- the synchronised window (outside the timed region, reported next to `value`, never as `value`): the same K closed-loop steps with
     # all environments in phase — free motion first half, every gripper closing at its middle, contact second half (`phases` splits it; round 4
-    # timed this one, enqueue-only, as `value`) — on a rollout of its own; the accounting runs below continue from the state it ends in
+    # timed this one, enqueue-only, as `value`) — on a rollout of its own; the accounting runs below continue from the state it ends in.
+    # Everything from here to the result line is --full only.
     sync_report, plog, ra = None, log, ro
-    if dephased and not args.stub:
+    if args.full and dephased and not args.stub:
         ra = BatchedRollout(args.config, close_at=close_sync, **kw_ro)
         for _ in range(args.warmup):
             ra.step()
@@ -456,7 +503,7 @@ def main():
     # rasterisation of step t on a second stream next to the substeps of step t+1 (BatchedRollout.set_pipelined) — what an open-loop stretch
     # (an action chunk) can run at
     pipe_report = None
-    if not args.stub and not args.no_pipelined:
+    if args.full and not args.stub and not args.no_pipelined:
         kp = max(4, min(args.steps, 10))
         rates = []
         for mode in (False, True):
@@ -477,152 +524,100 @@ def main():
                                "rasterisation of env step t on a second stream next to the substeps of step t+1; results are bit-identical (tested).  Valid when the "
                                "next action does not depend on this step's observation (inside an action chunk); never what `value` reports"}
 
-    # closed-loop accounting (outside the timed region): the same state, the same number of steps, first enqueue-only, then with get_obs() after
-    # every step — the ratio is what the policy's read costs (`value` is measured WITH it)
+    # closed-loop accounting (outside the timed region): the same state, the same number of steps, enqueue-only and with get_obs() after
+    # every step — the ratio is what the policy's read costs (`value` is measured WITH it).  The two modes alternate three times and each
+    # keeps its best run: a single short run of each in a fixed order carries the host / clock noise of its slot (small batches: a few ms)
     closed_report = None
-    if not args.stub:
-        kc = max(4, min(args.steps, 10))
-        rates = []
-        lossy0 = 0
-        for with_obs in (False, True):
-            for _ in range(2):
-                ra.step()
-            ra.get_obs()
-            torch.cuda.synchronize(dev)
-            lossy0 = ra.lossy_batches
-            t0c = time.perf_counter()
-            for _ in range(kc):
-                ra.step()
+    if args.full and not args.stub:
+        kc = max(8, min(args.steps, 10))
+        rates = [0.0, 0.0]
+        re_rendered_closed = 0
+        for _ in range(3):
+            for m, with_obs in enumerate((False, True)):
+                for _ in range(2):
+                    ra.step()
+                ra.get_obs()
+                torch.cuda.synchronize(dev)
+                lossy0 = ra.lossy_batches
+                t0c = time.perf_counter()
+                for _ in range(kc):
+                    ra.step()
+                    if with_obs:
+                        ra.get_obs()
+                torch.cuda.synchronize(dev)
+                rates[m] = max(rates[m], ra.n_env * kc / (time.perf_counter() - t0c))
                 if with_obs:
-                    ra.get_obs()
-            torch.cuda.synchronize(dev)
-            rates.append(ra.n_env * kc / (time.perf_counter() - t0c))
-        closed_report = {"env_steps_per_s": rates[1], "enqueue_only_env_steps_per_s": rates[0], "ratio": rates[1] / rates[0], "steps": kc,
-                         "re_rendered_batches": int(ra.lossy_batches - lossy0),
+                    re_rendered_closed += ra.lossy_batches - lossy0
+        closed_report = {"env_steps_per_s": rates[1], "enqueue_only_env_steps_per_s": rates[0], "ratio": rates[1] / rates[0], "steps": kc, "repeats": 3,
+                         "re_rendered_batches": int(re_rendered_closed),
                          "note": "this rank, after the synchronised window, in the state it ended in (contact): the same steps enqueue-only and with "
-                                 "get_obs() after every step (host waits for the frame, validates the sync-free raster batch, re-renders a lossy one)"}
+                                 "get_obs() after every step (host waits for the frame, validates the sync-free raster batch, re-renders a lossy one); "
+                                 "the modes alternate three times, each rate is the best of its three runs"}
     if ra is not ro:
         del ra
 
-    # cross-check for the roofline (untimed): the same env step captured as ONE kernel per batched substep, so that the
-    # HIP-event time / 667 is a per-kernel duration that rocprofv3's per-kernel average can be compared with directly
-    single_us = None
-    ro.phys.set_timing(True)
-    if ro.phys.layout_stats()["chains"] > 1:
-        ro.phys.set_tuning(chains=1)          # drops the captured graphs; the next steps re-capture with one chain
-        for _ in range(3):
-            ro.physics_step()
-        torch.cuda.synchronize(dev)
-        ms1, k1 = ro.phys.last_step_ms()
-        single_us = ms1 / max(k1, 1) * 1e3
-        ro.phys.set_tuning(chains=0)
-    # small batches: the same env step with the per-substep kernels of the same layout instead of the resident launch (untimed)
-    per_substep_us = None
-    if ro.phys.last_flavour().get("resident"):
-        ro.phys.set_resident(False)
-        best = None
-        for _ in range(6):                        # the first steps capture their graph flavour (both parities of the state buffer): best of six
-            ro.physics_step()
+    if args.full:
+        # cross-check for the roofline (untimed): the same env step captured as ONE kernel per batched substep, so that the
+        # HIP-event time / 667 is a per-kernel duration that rocprofv3's per-kernel average can be compared with directly
+        single_us = None
+        ro.phys.set_timing(True)
+        if ro.phys.layout_stats()["chains"] > 1:
+            ro.phys.set_tuning(chains=1)          # drops the captured graphs; the next steps re-capture with one chain
+            for _ in range(3):
+                ro.physics_step()
             torch.cuda.synchronize(dev)
             ms1, k1 = ro.phys.last_step_ms()
-            best = ms1 / max(k1, 1) * 1e3 if best is None else min(best, ms1 / max(k1, 1) * 1e3)
-        per_substep_us = {"avg_launch_us": best, "kernel": ro.phys.last_flavour()["kernel"],
-                          "note": "r2s_phys_set_resident(0): one launch per substep (large batches' flavour rule: deferred queries while anything is "
-                                  "within 3 cm of a mesh), best of six env steps after the timed region"}
-        ro.phys.set_resident(True)
-    ro.phys.set_timing(False)
+            single_us = ms1 / max(k1, 1) * 1e3
+            ro.phys.set_tuning(chains=0)
+        # small batches: the same env step with the per-substep kernels of the same layout instead of the resident launch (untimed)
+        per_substep_us = None
+        if ro.phys.last_flavour().get("resident"):
+            ro.phys.set_resident(False)
+            best = None
+            for _ in range(6):                        # the first steps capture their graph flavour (both parities of the state buffer): best of six
+                ro.physics_step()
+                torch.cuda.synchronize(dev)
+                ms1, k1 = ro.phys.last_step_ms()
+                best = ms1 / max(k1, 1) * 1e3 if best is None else min(best, ms1 / max(k1, 1) * 1e3)
+            per_substep_us = {"avg_launch_us": best, "kernel": ro.phys.last_flavour()["kernel"],
+                              "note": "r2s_phys_set_resident(0): one launch per substep (large batches' flavour rule: deferred queries while anything is "
+                                      "within 3 cm of a mesh), best of six env steps after the timed region"}
+            ro.phys.set_resident(True)
+        ro.phys.set_timing(False)
 
-    # stage timing of the raster pipeline (separate, untimed pass; drained first: the candidate rebuild of the last physics step runs
-    # on its own stream and would otherwise sit inside the stage events)
-    torch.cuda.synchronize(dev)
-    ro.raster.set_timing(True)
-    for _ in range(2):                      # the first timed render is the first synchronous one of the run (scratch re-sized on the host
-        ro.render()                         # between two stage events): the second is the one reported
+        # stage timing of the raster pipeline (separate, untimed pass; drained first: the candidate rebuild of the last physics step runs
+        # on its own stream and would otherwise sit inside the stage events)
         torch.cuda.synchronize(dev)
-    stages = ro.raster.stage_ms()
-    ro.raster.set_timing(False)
-    frames = ro.n_env * ro.views
-    raster_ms = sum(stages.values())
-    # realised scene statistics: visible Gaussians, instances, tile list lengths
-    dbg = ro.raster.debug()
-    tiles = ((ro.W + 15) // 16) * ((ro.H + 15) // 16)
-    from r2s_hip.raster import _memcpy_d2d
-    rng_t = torch.empty(frames * tiles, 2, dtype=torch.int32, device=dev)
-    _memcpy_d2d(rng_t.data_ptr(), dbg["ranges_ptr"], rng_t.numel() * 4, dev)
-    lens = (rng_t[:, 1] - rng_t[:, 0]).float()
-    scene = {"gaussians_per_frame": ro.P, "visible_fraction": float((dbg["radii"] > 0).float().mean()), "instances": int(dbg["num_rendered"]),
-             "tile_list_mean": float(lens.mean()), "tile_list_max": int(lens.max())}
-    # skinning (row f1): torch events are valid here, the kernels run on torch's current stream
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5):
-        ro._update_means()
-    e1.record()
-    torch.cuda.synchronize(dev)
-    skin_ms = e0.elapsed_time(e1) / 5
+        ro.raster.set_timing(True)
+        for _ in range(2):                      # the first timed render is the first synchronous one of the run (scratch re-sized on the host
+            ro.render()                         # between two stage events): the second is the one reported
+            torch.cuda.synchronize(dev)
+        stages = ro.raster.stage_ms()
+        ro.raster.set_timing(False)
+        frames = ro.n_env * ro.views
+        raster_ms = sum(stages.values())
+        # realised scene statistics: visible Gaussians, instances, tile list lengths
+        dbg = ro.raster.debug()
+        tiles = ((ro.W + 15) // 16) * ((ro.H + 15) // 16)
+        from r2s_hip.raster import _memcpy_d2d
+        rng_t = torch.empty(frames * tiles, 2, dtype=torch.int32, device=dev)
+        _memcpy_d2d(rng_t.data_ptr(), dbg["ranges_ptr"], rng_t.numel() * 4, dev)
+        lens = (rng_t[:, 1] - rng_t[:, 0]).float()
+        scene = {"gaussians_per_frame": ro.P, "visible_fraction": float((dbg["radii"] > 0).float().mean()), "instances": int(dbg["num_rendered"]),
+                 "tile_list_mean": float(lens.mean()), "tile_list_max": int(lens.max())}
+        # skinning (row f1): torch events are valid here, the kernels run on torch's current stream
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            ro._update_means()
+        e1.record()
+        torch.cuda.synchronize(dev)
+        skin_ms = e0.elapsed_time(e1) / 5
 
     if rank == 0:
         value = total_envs * args.steps / elapsed
         n_sub = args.substeps
-        phys_ms = sum(log["phys_ms"]) / args.steps                 # mean physics graph time per env step over the timed window
-        t_kernel = phys_ms * 1e-3 / n_sub
-        alg_bytes = ro.physics_algorithmic_bytes_per_substep()
-        chains = ro.phys.layout_stats()["chains"]
-        achieved = alg_bytes / t_kernel / 1e9
-        comp_bytes = ro.composite_algorithmic_bytes()
-        comp_gbs = comp_bytes / (stages["composite"] * 1e-3) / 1e9 if stages["composite"] > 0 else 0.0
-
-        def phase(sel):   # of the SYNCHRONISED window (the timed one itself when it was not de-phased)
-            idx = [i for i in range(args.steps) if sel(i)]
-            if not idx:
-                return None
-            return {"steps": len(idx), "ms_per_step": sum(plog["step_ms"][i] for i in idx) / len(idx),
-                    "physics_ms_per_step": sum(plog["phys_ms"][i] for i in idx) / len(idx),
-                    "substep_us": sum(plog["phys_ms"][i] for i in idx) / len(idx) / n_sub * 1e3,
-                    "self_collision_candidates": int(max(plog["candidates"][i] for i in idx)),
-                    "mesh_contacts": int(max(plog["mesh_hits"][i] for i in idx)),
-                    "grasped_envs": int(max(plog["grasped"][i] for i in idx)),
-                    "kernel_flavours": sorted({plog["flavour"][i] for i in idx})}
-
-        resident_steps = sum("k_steps_resident" in f for f in log["flavour"])   # env steps of the window that ran as one resident launch
         first_contact = (close_sync if dephased else ro.close_at) - args.warmup + (1 if ramp else 0)  # index in the synchronised window of the step in which the pads reach the object (the ramp's second step: the first particles enter the pads' margins) / the fingers snap shut / the rod arrives
-        (pmc_sub, src), (pmc_comp, _) = pmc_summary("k_substep", args.config), pmc_summary("k_composite", args.config)
-        shared_bytes = 16 * ro.S + 48 * ro.N * ro.n_env        # the topology once (it is shared by the environments and L2-resident) + every environment's state
-        traffic = pmc_sub["hbm_bytes_per_launch"] if pmc_sub and ro.n_env == 32 and n_sub == 667 else None
-        roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "frac_shared_topology": shared_bytes / t_kernel / 1e9 / HBM_PEAK_GBS,
-                "shared_topology_bytes_per_launch": shared_bytes,
-                "traffic_over_shared": (traffic / shared_bytes) if traffic else None,
-                "bound_in_practice": "VALU issue + dependent latency (valu_busy_frac of the SIMD issue cycles; hbm_actual_frac of the HBM peak): neither "
-                                     "pipe is saturated — `frac` is the SURVEY.md §8d CONTRACT figure (every environment charged its own copy of the "
-                                     "topology), `frac_shared_topology` charges the topology once and is the physical lower bound on HBM bytes",
-                "traffic": traffic,
-                "traffic_source": src if pmc_sub else None,
-                "hbm_actual_frac": (pmc_sub["hbm_bytes_per_launch"] / t_kernel / 1e9 / HBM_PEAK_GBS) if pmc_sub and ro.n_env == 32 and n_sub == 667 else None,
-                "valu_busy_frac": pmc_sub.get("valu_busy_frac") if pmc_sub else None,
-                # the kernel's own arithmetic bound: its VALU instructions x 4 issue cycles over the chip's 1024 SIMDs, as a share of the
-                # kernel's span — the same ratio as valu_busy_frac, named for what it says: 1 / valu_floor_frac is how far the kernel runs above its VALU floor
-                "valu_floor_frac": pmc_sub.get("valu_busy_frac") if pmc_sub else None,
-                "valu_floor_us": (pmc_sub["counters_mean_per_dispatch"]["SQ_INSTS_VALU"] * 4 / 1024 / 2.4e3) if pmc_sub and "SQ_INSTS_VALU" in pmc_sub.get("counters_mean_per_dispatch", {}) else None,
-                "read_requests_reaching_dram_frac": pmc_sub.get("read_requests_reaching_dram_frac") if pmc_sub else None,
-                "counters_stale": pmc_sub.get("stale") if pmc_sub else None,
-                "kernel": ("k_steps_resident (small batch: all substeps of an env step in ONE launch; the figures below are per substep of it)" if resident_steps == args.steps
-                           else "k_substep (fused spring gather + velocity + collisions + integrate)"),
-                "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": t_kernel * 1e6, "launches": n_sub * args.steps,
-                "resident_env_steps": resident_steps, "per_substep_kernels_check": per_substep_us,
-                "concurrent_chains": chains,
-                "single_chain_check": None if single_us is None else {
-                    "avg_launch_us": single_us, "achieved": alg_bytes / (single_us * 1e-6) / 1e9, "frac": alg_bytes / (single_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                    "note": "same step with one kernel per batched substep (r2s_phys_set_tuning chains=1, measured after the timed region, "
-                            "in the contact state the window ended in): a per-kernel duration, comparable with profiles/r3_bench_kernel_stats_chains1.md (that table is of the free + contact window, this figure of the contact state alone)"},
-                "note": f"frac is the SURVEY.md §8d contract figure: algorithmic bytes (16 S + 48 N per env) / avg launch time / 8 TB/s, averaged over "
-                        f"the whole timed window (free + contact).  The topology (16 S) is shared by the {ro.n_env} envs and stays in L2, so the bytes that "
-                        "reach HBM are hbm_actual_frac of peak; valu_busy_frac = SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x kernel span), the share of SIMD issue cycles spent on VALU instructions: the kernel is "
-                        f"VALU-issue / latency bound, not HBM bound.  One 'launch' = one batched substep of all {ro.n_env} envs, issued as {chains} concurrent "
-                        "kernels over disjoint env ranges, each chain its own captured graph on its own stream (per-kernel durations overlap); avg_launch_us = HIP-event time of the 667-substep step / 667"}
-        if roof["frac"] > 1.0:
-            roof["frac_exceeds_one"] = ("the contract charges 16 S bytes of topology PER ENVIRONMENT; the environments share one copy that stays in L2, so "
-                                        "the contract figure is not bounded by 1 — read frac_shared_topology / hbm_actual_frac for the physical picture")
         out = {
             "metric": "sim env-steps/sec (phys+render) per node at 32 envs", "value": value, "unit": "env-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -642,30 +637,95 @@ def main():
                                "raster batch, re-renders a lossy one) before the next step is applied; environment e runs the action trace (e K) // E steps late.  Gripper "
                                "scenes: the commanded opening ramps down by close_rate per step from 4 steps before the window on, the pads load up, the grasp state machine "
                                "latches from the stepper's own forces (grasped_envs_per_step) and the object is lifted in the grasp; step_latency_ms = host wall clock per step"},
-            "phases": {"free": phase(lambda i: i < first_contact), "contact": phase(lambda i: i >= first_contact),
-                       "window": "synchronised_window" if dephased else "the timed window",
-                       "note": "free = the end effector moves, nothing touches; contact = fingers closed on the toy's arms / rod against the block "
-                               "(mesh_contacts = particles inside a collision margin in the last substep, self_collision_candidates = particles "
-                               "with live candidates, maxima over the phase's steps)"},
-            "parity_gate": gate if gate is not None else {"passed": None, "note": "skipped (--no-parity-gate)"},
-            "roofline": roof,
-            "raster": {"gs_raster_mpix_per_s": frames * ro.W * ro.H / (raster_ms * 1e-3) / 1e6, "frames": frames,
-                       "num_rendered": int(ro.last_num_rendered), "stage_ms": stages, "scene": scene,
-                       "lossy_batches": int(ro.lossy_batches),   # sync-free batches whose instance count outgrew the capacity (must be 0)
-                       "composite_roofline": {"bound": "hbm", "achieved": comp_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                              "frac": comp_gbs / HBM_PEAK_GBS, "algorithmic_bytes": comp_bytes,
-                                              "traffic": pmc_comp["hbm_bytes_per_launch"] if pmc_comp and ro.n_env == 32 else None,
-                                              "traffic_source": src if pmc_comp else None,
-                                              "valu_busy_frac": pmc_comp.get("valu_busy_frac") if pmc_comp else None,
-                                              "note": "VALU/exp-bound (≈115 flop per algorithmic byte, SURVEY.md §7): the north_star's >= 0.60 of HBM peak "
-                                                      "is not reachable for this kernel at any instruction count above ~1/3 of the reference's per-pixel "
-                                                      "arithmetic; valu_busy_frac (SQ_INSTS_VALU x 4 cycles over the SIMD cycles of the kernel span, at most 1) is the figure that says how close to its real bound it runs"}},
-            "physics_ms_per_env_step": phys_ms, "skinning_ms_per_env_step": skin_ms,
             "construct_s_per_rank": [round(float(x), 3) for x in records[:, 5]],   # outside the timed region; every rank builds, captures and settles its own batch
             "task_success": {"envs_satisfying_predicate": int(records[:, 4].sum().item()), "of": total_envs,
                              "note": "frame-level success predicate of the scene's task evaluated on the device after the last step "
                                      "(synthetic action trace: not a policy result)"},
         }
+        if args.full:
+            phys_ms = sum(log["phys_ms"]) / args.steps                 # mean physics graph time per env step over the timed window
+            t_kernel = phys_ms * 1e-3 / n_sub
+            alg_bytes = ro.physics_algorithmic_bytes_per_substep()
+            chains = ro.phys.layout_stats()["chains"]
+            achieved = alg_bytes / t_kernel / 1e9
+            comp_bytes = ro.composite_algorithmic_bytes()
+            comp_gbs = comp_bytes / (stages["composite"] * 1e-3) / 1e9 if stages["composite"] > 0 else 0.0
+
+            def phase(sel):   # of the SYNCHRONISED window (the timed one itself when it was not de-phased)
+                idx = [i for i in range(args.steps) if sel(i)]
+                if not idx:
+                    return None
+                return {"steps": len(idx), "ms_per_step": sum(plog["step_ms"][i] for i in idx) / len(idx),
+                        "physics_ms_per_step": sum(plog["phys_ms"][i] for i in idx) / len(idx),
+                        "substep_us": sum(plog["phys_ms"][i] for i in idx) / len(idx) / n_sub * 1e3,
+                        "self_collision_candidates": int(max(plog["candidates"][i] for i in idx)),
+                        "mesh_contacts": int(max(plog["mesh_hits"][i] for i in idx)),
+                        "grasped_envs": int(max(plog["grasped"][i] for i in idx)),
+                        "kernel_flavours": sorted({plog["flavour"][i] for i in idx})}
+
+            resident_steps = sum("k_steps_resident" in f for f in log["flavour"])   # env steps of the window that ran as one resident launch
+            (pmc_sub, src), (pmc_comp, _) = pmc_summary("k_substep", args.config), pmc_summary("k_composite", args.config)
+            shared_bytes = 16 * ro.S + 48 * ro.N * ro.n_env        # the topology once (it is shared by the environments and L2-resident) + every environment's state
+            traffic = pmc_sub["hbm_bytes_per_launch"] if pmc_sub and ro.n_env == 32 and n_sub == 667 else None
+            roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "frac_shared_topology": shared_bytes / t_kernel / 1e9 / HBM_PEAK_GBS,
+                    "shared_topology_bytes_per_launch": shared_bytes,
+                    "traffic_over_shared": (traffic / shared_bytes) if traffic else None,
+                    "bound_in_practice": "VALU issue + dependent latency (valu_busy_frac of the SIMD issue cycles; hbm_actual_frac of the HBM peak): neither "
+                                         "pipe is saturated — `frac` is the SURVEY.md §8d CONTRACT figure (every environment charged its own copy of the "
+                                         "topology), `frac_shared_topology` charges the topology once and is the physical lower bound on HBM bytes",
+                    "traffic": traffic,
+                    "traffic_source": src if pmc_sub else None,
+                    "hbm_actual_frac": (pmc_sub["hbm_bytes_per_launch"] / t_kernel / 1e9 / HBM_PEAK_GBS) if pmc_sub and ro.n_env == 32 and n_sub == 667 else None,
+                    "valu_busy_frac": pmc_sub.get("valu_busy_frac") if pmc_sub else None,
+                    # the kernel's own arithmetic bound: its VALU instructions x 4 issue cycles over the chip's 1024 SIMDs, as a share of the
+                    # kernel's span — the same ratio as valu_busy_frac, named for what it says: 1 / valu_floor_frac is how far the kernel runs above its VALU floor
+                    "valu_floor_frac": pmc_sub.get("valu_busy_frac") if pmc_sub else None,
+                    "valu_floor_us": (pmc_sub["counters_mean_per_dispatch"]["SQ_INSTS_VALU"] * 4 / 1024 / 2.4e3) if pmc_sub and "SQ_INSTS_VALU" in pmc_sub.get("counters_mean_per_dispatch", {}) else None,
+                    "read_requests_reaching_dram_frac": pmc_sub.get("read_requests_reaching_dram_frac") if pmc_sub else None,
+                    "counters_stale": pmc_sub.get("stale") if pmc_sub else None,
+                    "kernel": ("k_steps_resident (small batch: all substeps of an env step in ONE launch; the figures below are per substep of it)" if resident_steps == args.steps
+                               else "k_substep (fused spring gather + velocity + collisions + integrate)"),
+                    "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": t_kernel * 1e6, "launches": n_sub * args.steps,
+                    "resident_env_steps": resident_steps, "per_substep_kernels_check": per_substep_us,
+                    "concurrent_chains": chains,
+                    "single_chain_check": None if single_us is None else {
+                        "avg_launch_us": single_us, "achieved": alg_bytes / (single_us * 1e-6) / 1e9, "frac": alg_bytes / (single_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                        "note": "same step with one kernel per batched substep (r2s_phys_set_tuning chains=1, measured after the timed region, "
+                                "in the contact state the window ended in): a per-kernel duration, comparable with profiles/r3_bench_kernel_stats_chains1.md (that table is of the free + contact window, this figure of the contact state alone)"},
+                    "note": f"frac is the SURVEY.md §8d contract figure: algorithmic bytes (16 S + 48 N per env) / avg launch time / 8 TB/s, averaged over "
+                            f"the whole timed window (free + contact).  The topology (16 S) is shared by the {ro.n_env} envs and stays in L2, so the bytes that "
+                            "reach HBM are hbm_actual_frac of peak; valu_busy_frac = SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x kernel span), the share of SIMD issue cycles spent on VALU instructions: the kernel is "
+                            f"VALU-issue / latency bound, not HBM bound.  One 'launch' = one batched substep of all {ro.n_env} envs, issued as {chains} concurrent "
+                            "kernels over disjoint env ranges, each chain its own captured graph on its own stream (per-kernel durations overlap); avg_launch_us = HIP-event time of the 667-substep step / 667"}
+            if roof["frac"] > 1.0:
+                roof["frac_exceeds_one"] = ("the contract charges 16 S bytes of topology PER ENVIRONMENT; the environments share one copy that stays in L2, so "
+                                            "the contract figure is not bounded by 1 — read frac_shared_topology / hbm_actual_frac for the physical picture")
+            out.update({
+                "phases": {"free": phase(lambda i: i < first_contact), "contact": phase(lambda i: i >= first_contact),
+                           "window": "synchronised_window" if dephased else "the timed window",
+                           "note": "free = the end effector moves, nothing touches; contact = fingers closed on the toy's arms / rod against the block "
+                                   "(mesh_contacts = particles inside a collision margin in the last substep, self_collision_candidates = particles "
+                                   "with live candidates, maxima over the phase's steps)"},
+                "parity_gate": gate if gate is not None else {"passed": None, "note": "skipped (--no-parity-gate)"},
+                "roofline": roof,
+                "raster": {"gs_raster_mpix_per_s": frames * ro.W * ro.H / (raster_ms * 1e-3) / 1e6, "frames": frames,
+                           "num_rendered": int(ro.last_num_rendered), "stage_ms": stages, "scene": scene,
+                           "lossy_batches": int(ro.lossy_batches),   # sync-free batches whose instance count outgrew the capacity (must be 0)
+                           "composite_roofline": {"bound": "hbm", "achieved": comp_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                                  "frac": comp_gbs / HBM_PEAK_GBS, "algorithmic_bytes": comp_bytes,
+                                                  "traffic": pmc_comp["hbm_bytes_per_launch"] if pmc_comp and ro.n_env == 32 else None,
+                                                  "traffic_source": src if pmc_comp else None,
+                                                  "valu_busy_frac": pmc_comp.get("valu_busy_frac") if pmc_comp else None,
+                                                  "note": "VALU/exp-bound (≈115 flop per algorithmic byte, SURVEY.md §7): the north_star's >= 0.60 of HBM peak "
+                                                          "is not reachable for this kernel at any instruction count above ~1/3 of the reference's per-pixel "
+                                                          "arithmetic; valu_busy_frac (SQ_INSTS_VALU x 4 cycles over the SIMD cycles of the kernel span, at most 1) is the figure that says how close to its real bound it runs"}},
+                "physics_ms_per_env_step": phys_ms, "skinning_ms_per_env_step": skin_ms,
+            })
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                              "note": "the last timed step as get_obs() hands it out + the particle state, float32 .npy; per array [shape written, "
+                                      "shape computed]: a flat shape is a seeded sample of the array's elements (bench.dump_outputs)"}
         if sink_report is not None:
             out["observation_sink"] = sink_report
         if pipe_report is not None:
@@ -684,13 +744,13 @@ def main():
             out["value_withheld"] = out["value"]
             out["value"] = None
             out["note"] = "PARITY GATE FAILED: the throughput of a path whose results differ from the reference's is not a result (see parity_gate)"
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(ro, args.cpu_budget)
             except Exception as e:  # the baseline is a report, never the product
                 out["cpu_baseline"] = {"value": None, "unit": "env-steps/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
         n_epi = args.episodes if args.episodes >= 0 else (2 if world == 1 else 0)
-        if n_epi > 0 and not args.stub:
+        if args.full and n_epi > 0 and not args.stub:
             ro = None
             torch.cuda.empty_cache()
             epi = []

@@ -1,9 +1,10 @@
-"""bench.py keeps the driver's contract: one JSON line with the agreed keys, roofline and cpu_baseline objects."""
+"""bench.py keeps the driver's contract: one JSON line with the agreed keys; with --full, roofline and cpu_baseline objects."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny", "--steps", "2", "--warmup", "1", "--substeps", "30",
-                          "--cpu-budget", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cpu-budget", "2", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -47,7 +48,8 @@ def test_headline_schedule_contains_free_motion_finger_contact_and_live_self_col
     latches from the stepper's own forces inside the window) particles are inside the fingers' collision margin, then live
     self-collision candidates (the toy's arms pressed together) and the graph flavour with the self-collision variant of the fused
     kernel plus the finishing code, and the grasp state machine latches: the window's last steps are the held grasp."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--envs", "2", "--steps", "16", "--warmup", "2", "--no-cpu-baseline", "--episodes", "0"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--envs", "2", "--steps", "16", "--warmup", "2", "--no-cpu-baseline", "--episodes", "0",
+                          "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][-1])
@@ -60,3 +62,31 @@ def test_headline_schedule_contains_free_motion_finger_contact_and_live_self_col
     assert any(",true," in f and ("k_contact_finish" in f or "k_substep_pf" in f) for f in contact["kernel_flavours"]), contact["kernel_flavours"]
     assert all(",true," not in f for f in free["kernel_flavours"]), free["kernel_flavours"]
     assert "sloth_32env" in d["config"]["workload"] and "grasp" in d["config"]["workload"]
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) sets up, warms up, times --steps steps and prints the headline line, with nothing that takes work
+    of its own (gate, other windows, per-kernel figures, CPU baseline, episodes).  --dump-outputs writes what the last timed step
+    computed as float32 .npy within 64 MB, and two runs with the same arguments write the same arrays."""
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny", "--steps", "3", "--warmup", "1", "--substeps", "30",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs.append((json.loads(lines[0]), d))
+    r, d = runs[0]
+    for k, t in dict(metric=str, value=float, unit=str, ms_per_step=float, higher_is_better=bool, dtype=str).items():
+        assert isinstance(r[k], t), (k, r[k])
+    assert r["steps"] == 3 and r["warmup"] == 1 and len(r["window"]["step_latency_ms"]["per_step"]) == 3
+    assert abs(r["value"] - r["config"]["envs_per_gpu"] * 1000.0 / r["ms_per_step"]) < 1e-6 * r["value"]
+    for k in ("parity_gate", "phases", "roofline", "raster", "cpu_baseline", "episodes", "synchronised_window", "throughput_mode", "closed_loop_get_obs"):
+        assert k not in r, k
+    files = sorted(os.listdir(d))
+    assert files == sorted(f"{n}.npy" for n in r["outputs"]["arrays"]) and {"image_0.npy", "depth_0.npy", "particles_x.npy"} <= set(files)
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(d / f), np.load(runs[1][1] / f)
+        assert a.dtype == np.float32 and a.size > 0 and np.array_equal(a, b, equal_nan=True), f

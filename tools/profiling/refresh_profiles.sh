@@ -8,12 +8,12 @@ cd $R
 rm -f gpurun_out/r2_parity.json
 timeout 900 python -m pytest tests -m gpu -q > $out/pytest.log 2>&1; echo "pytest rc $?" >> $out/pytest.log; tail -3 $out/pytest.log
 cp gpurun_out/r2_parity.json $out/r2_parity.json
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_sloth_32env.json 2> $out/bench.err; tail -c 600 $out/bench_sloth_32env.json; echo
+timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_sloth_32env.json 2> $out/bench.err; tail -c 600 $out/bench_sloth_32env.json; echo
 : > $out/bench_other_configs.jsonl
 for cfg in rope_1env T_32env T_pusher_32env sloth_multicam_8env; do
-  timeout 300 python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $out/bench_other_configs.jsonl
+  timeout 300 python bench.py --config $cfg --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | tail -1 >> $out/bench_other_configs.jsonl
 done
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --sink /tmp/r2_sink 2>/dev/null | tail -1 >> $out/bench_other_configs.jsonl
+timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --sink /tmp/r2_sink 2>/dev/null | tail -1 >> $out/bench_other_configs.jsonl
 python - <<'PY'
 import json
 for l in open('gpurun_out/prof_r2/bench_other_configs.jsonl'):
@@ -22,7 +22,7 @@ PY
 cd /tmp && export TMPDIR=/tmp
 for mode in default chains1; do
   if [ $mode = chains1 ]; then export R2S_CHAINS=1; else unset R2S_CHAINS; fi
-  timeout 400 rocprofv3 --kernel-trace --stats -d $out/trace_$mode -o bench -- python $R/bench.py --steps 6 --warmup 3 --no-cpu-baseline > $out/bench_trace_$mode.log 2>&1 || echo trace-failed
+  timeout 400 rocprofv3 --kernel-trace --stats -d $out/trace_$mode -o bench -- python $R/bench.py --steps 6 --warmup 3 --full --no-cpu-baseline > $out/bench_trace_$mode.log 2>&1 || echo trace-failed
   db=$(find $out/trace_$mode -name "*.db" | head -1)
   python $R/tools/rocpd_stats.py $db $out/kernel_stats_$mode.md > /dev/null 2>&1 || echo stats-failed
   head -9 $out/kernel_stats_$mode.md | cut -c1-70,150-240
@@ -30,7 +30,7 @@ for mode in default chains1; do
 done
 unset R2S_CHAINS
 # the large-mesh finishing kernel (k_contact_finish<2>) in its own table: the pusher workload, second half of the window in contact
-timeout 400 rocprofv3 --kernel-trace --stats -d $out/trace_pusher -o bench -- python $R/bench.py --config T_pusher_32env --steps 6 --warmup 3 --no-cpu-baseline > $out/bench_trace_pusher.log 2>&1 || echo trace-failed
+timeout 400 rocprofv3 --kernel-trace --stats -d $out/trace_pusher -o bench -- python $R/bench.py --config T_pusher_32env --steps 6 --warmup 3 --full --no-cpu-baseline > $out/bench_trace_pusher.log 2>&1 || echo trace-failed
 db=$(find $out/trace_pusher -name "*.db" | head -1)
 python $R/tools/rocpd_stats.py $db $out/kernel_stats_pusher.md > /dev/null 2>&1 || echo stats-failed
 head -6 $out/kernel_stats_pusher.md | cut -c1-70,150-240
