@@ -10,25 +10,47 @@ import numpy as np
 EPS32 = float(np.finfo(np.float32).eps)
 
 
-def bone_rotations(bones, motions, relations):
+def bone_offsets(bones, motions, relations):
+    """(a_k, a'_k): every bone's float32 offsets to its k neighbours before / after the motion (:79-80), each (n,k,3)."""
+    bones = np.asarray(bones, np.float32); motions = np.asarray(motions, np.float32)
+    rel = np.asarray(relations)
+    adj = (bones[rel] - bones[:, None]).astype(np.float32)                                       # :79
+    adj_new = ((bones[rel] + motions[rel]) - (bones[:, None] + motions[:, None])).astype(np.float32)  # :80
+    return adj, adj_new
+
+
+def fit_matrices(bones, motions, relations, how):
+    """F = sum_k a'_k a_k^T of the SAME float32 offsets as bone_rotations, summed another way — to measure how far the rounding
+    of that sum alone moves a rotation (tests/test_lbs_edges_gpu.py): 'f32_ascending' / 'f32_descending' add the float32
+    products one neighbour at a time, k = 0.. or k = K-1..; 'f64' multiplies and adds in float64 (and returns float64)."""
+    adj, adj_new = bone_offsets(bones, motions, relations)
+    if how == "f64":
+        return np.einsum("nki,nkj->nij", adj_new.astype(np.float64), adj.astype(np.float64))
+    ks = {"f32_ascending": range(adj.shape[1]), "f32_descending": range(adj.shape[1] - 1, -1, -1)}[how]
+    F = np.zeros((len(adj), 3, 3), np.float32)
+    for k in ks:
+        F = (F + (adj_new[:, k, :, None] * adj[:, k, None, :]).astype(np.float32)).astype(np.float32)
+    return F
+
+
+def bone_rotations(bones, motions, relations, F=None, dtype=np.float32):
     """Per-bone rotation of transform_utils.py:73-165: Kabsch fit of the bone's k neighbours before / after the motion.
 
     F = sum_k (a'_k)(a_k)^T (:83); rank by torch.linalg.matrix_rank's default tolerance max(m,n)*eps*sigma_max (:85);
     rank 2 or 3: R = U S V^T with S flipped so that det R = +1 (:96-114), i.e. the proper rotation closest to F.
     If ANY bone has rank < 2 the reference's assignment `bone_transforms[:, :3, :3] = R` (:157) fails on the shape
-    mismatch and its `except` branch sets every rotation to the identity (:159-162); reproduced here."""
-    bones = np.asarray(bones, np.float32); motions = np.asarray(motions, np.float32)
-    rel = np.asarray(relations)
-    adj = (bones[rel] - bones[:, None]).astype(np.float32)                                       # :79
-    adj_new = ((bones[rel] + motions[rel]) - (bones[:, None] + motions[:, None])).astype(np.float32)  # :80
-    F = np.einsum("nki,nkj->nij", adj_new, adj).astype(np.float32)                                # :83  (n,3,3)
-    U, S, Vt = np.linalg.svd(F.astype(np.float64))
+    mismatch and its `except` branch sets every rotation to the identity (:159-162); reproduced here.
+    `F` (n,3,3), if given, replaces the sum (see fit_matrices); `dtype` is that of the returned rotations."""
+    if F is None:
+        adj, adj_new = bone_offsets(bones, motions, relations)
+        F = np.einsum("nki,nkj->nij", adj_new, adj).astype(np.float32)                            # :83  (n,3,3)
+    U, S, Vt = np.linalg.svd(np.asarray(F).astype(np.float64))
     rank = (S > (3 * EPS32 * S[:, :1])).sum(1)
     if not np.all(rank >= 2):
-        return np.tile(np.eye(3, dtype=np.float32), (len(bones), 1, 1)), rank
+        return np.tile(np.eye(3, dtype=dtype), (len(F), 1, 1)), rank
     d = np.sign(np.linalg.det(U) * np.linalg.det(Vt))
-    D = np.tile(np.eye(3), (len(bones), 1, 1)); D[:, 2, 2] = d
-    return (U @ D @ Vt).astype(np.float32), rank
+    D = np.tile(np.eye(3), (len(F), 1, 1)); D[:, 2, 2] = d
+    return (U @ D @ Vt).astype(dtype), rank
 
 
 def interpolate_motions(bones, motions, relations, xyz, weights, weights_indices):
